@@ -12,8 +12,19 @@ tokens, completion mask, rewards, group advantages, policy forward + fused
 log-prob/entropy + fused loss + backward, (N>1: RCCL gradient all-reduce),
 grad-norm clip and AdamW.  Weak scaling: per-GPU work is fixed as N grows.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--no-cpu-baseline]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full [--no-cpu-baseline]]
     torchrun --nproc-per-node N --master-addr 127.0.0.1 bench.py --gpus N ...
+
+A plain run sets up, warms up, times the K steps and prints the result line
+(metric, value, unit, ms_per_step, ...).  `--full` adds what takes runs of its
+own: the per-kernel `roofline` object (HIP events around the eager kernels in
+the timed region, then each decode kernel replayed alone) and the
+`cpu_baseline` object (the oracle's CPU restatement, N = 1 only).
+`--dump-outputs DIR` writes what the last timed step computed as
+DIR/<name>.npy (rank 0): its loss and gradient norm, the completions and
+advantages it trained on, and fixed seeded samples of the updated weights and
+of the gradient.  The inputs depend only on the arguments, so two builds can be
+compared output for output.
 
 `--gpus N` without torchrun's environment: this process never touches the
 GPU; it starts `torch.distributed.run` with N ranks (one per GPU, RCCL) as a
@@ -191,6 +202,29 @@ def kernel_roofline(kern: dict, eng, steps: int, C: int) -> dict:
                             for k, v in kinfo.items()}}
 
 
+DUMP_SAMPLE = 4 << 20  # elements sampled from each flat buffer (16 MB as float32)
+
+
+def dump_outputs(path: str, tr, out: dict) -> None:
+    """`--dump-outputs`: the arrays the last timed step handed back or left behind,
+    one float32 / float64 .npy each (about 33 MB in all).  `out` is the return of
+    that `training_step_group()`; the rollout it trained on is the trainer's
+    buffered generation; weights and gradient are sampled at fixed seeded indices."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    arrays = {k: out[k].detach().double().reshape(1) for k in ("loss", "grad_norm")}
+    for k in ("completion_ids", "completion_mask", "advantages"):
+        arrays[k] = torch.cat([mb[k] for mb in tr._buffered_inputs]).double()
+    flat, grad = tr.model.flat, tr.model.grad
+    n = flat.numel()
+    idx = torch.randint(0, n, (min(DUMP_SAMPLE, n),), generator=torch.Generator().manual_seed(4321)).sort().values
+    idx = idx.to(flat.device)
+    arrays["weights_sample"] = flat[idx].float()
+    arrays["grad_sample"] = grad[idx].float()
+    for k, v in arrays.items():
+        np.save(os.path.join(path, k + ".npy"), v.cpu().numpy())
+
+
 def _launch_ranks(n: int, argv: list) -> int:
     """Start N ranks under torch.distributed.run (127.0.0.1 rendezvous) as a
     child process; this parent has not initialised the GPU and never does."""
@@ -207,7 +241,11 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=3)
     ap.add_argument("--warmup", type=int, default=2)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure the per-kernel roofline object and the CPU baseline (runs of their own)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave the CPU baseline out")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs as DIR/<name>.npy")
     ap.add_argument("--layers", type=int, default=None, help="debug only: shrink the model (invalid for reporting)")
     ap.add_argument("--variant", choices=("default", "top_p", "greedy"), default="default",
                     help="SURVEY.md §8d cfg2 sampling variants: top_p 0.9, or greedy decoding")
@@ -255,22 +293,23 @@ def main():
     sd.barrier()
     torch.cuda.synchronize()
     profiling.reset()
-    profiling.enable(True)
+    profiling.enable(args.full)  # per-launch HIP events feed the roofline object only
+    out = None
     t0 = time.perf_counter()
     for _ in range(steps):
-        tr.training_step_group()
+        out = tr.training_step_group()
     torch.cuda.synchronize()
     sd.barrier()
     elapsed = time.perf_counter() - t0
     profiling.enable(False)
     elapsed = sd.all_max(elapsed)
-    kern = profiling.summary()
+    if args.dump_outputs and rank == 0 and out is not None:
+        dump_outputs(args.dump_outputs, tr, out)
     log = tr._flush_logs()
     samples = world * PROMPTS_PER_GPU * G * steps
     value = samples / elapsed
     ms = 1000.0 * elapsed / steps
 
-    roof = kernel_roofline(kern, getattr(tr, "_engine", None), steps, C)
     # step-level roofline: t_roof = HBM bytes / 8 TB/s + FLOPs / 2.5 PF
     t_roof_ms = 70.5
     line = {"metric": METRIC, "value": round(value, 3), "unit": "samples/s", "n_gpus": world, "steps": steps,
@@ -284,10 +323,11 @@ def main():
                        "prompts_per_gpu": PROMPTS_PER_GPU, "num_generations": G, "prompt_len": P,
                        "completion_len": C, "seq_len": P + C, "micro_batch": MB, "grad_accum": GA, "beta": 0.0,
                        "parallelism": f"dp{world}", "layers": cfg.num_hidden_layers},
-            "roofline": roof,
             "step_roofline": {"t_roof_ms_per_gpu": t_roof_ms, "frac": round(t_roof_ms / ms, 4)},
             "train_log": {k: log.get(k) for k in ("loss", "grad_norm", "reward", "entropy")}}
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and not args.layers:
+    if args.full:
+        line["roofline"] = kernel_roofline(profiling.summary(), getattr(tr, "_engine", None), steps, C)
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline and not args.layers:
         try:
             line["cpu_baseline"] = cpu_baseline(f"GPU run: {steps} timed steps")
         except Exception as e:  # report, never hide

@@ -1,5 +1,5 @@
 """Live per-kernel timing with HIP events (torch.cuda.Event records on the
-same stream the C-ABI kernels are launched on).  Off by default; bench.py
+same stream the C-ABI kernels are launched on).  Off by default; `bench.py --full`
 switches it on for the timed region.  Replaces the reference's wall-clock
 `profiling_context` (trl/extras/profiling.py:31-100) for device work."""
 from __future__ import annotations

@@ -275,6 +275,35 @@ def test_bench_launches_n_ranks_itself(n):
     assert line["config"]["global_batch"] == 64 * n and line["value"] > 0
 
 
+def test_bench_plain_run_is_lean_and_dumps_its_outputs(tmp_path):
+    """A plain `bench.py` run prints the headline figures without the objects that take
+    runs of their own (`roofline`, `cpu_baseline`: `--full`), honours `--steps`, and with
+    `--dump-outputs DIR` leaves the last timed step's arrays as float32 / float64 .npy
+    files of at most 64 MB in all.  Two layers: the option handling is what is tested."""
+    import numpy as np
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK")}
+    r = subprocess.run([sys.executable, "bench.py", "--gpus", "1", "--layers", "2", "--steps", "2", "--warmup", "1",
+                        "--dump-outputs", str(tmp_path / "out")], cwd=root, env=env, capture_output=True, text=True,
+                       timeout=600)
+    assert r.returncode == 0, r.stderr[-4000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, r.stdout[-2000:]
+    line = json.loads(lines[0])
+    assert "roofline" not in line and "cpu_baseline" not in line
+    assert line["steps"] == 2 and line["unit"] == "samples/s" and line["higher_is_better"] is True
+    assert line["dtype"] == "bf16" and line["ms_per_step"] > 0
+    assert abs(line["value"] - 64 / (line["ms_per_step"] / 1000.0)) <= 0.01 * line["value"]
+    got = {f[:-4]: np.load(tmp_path / "out" / f) for f in os.listdir(tmp_path / "out")}
+    assert set(got) == {"loss", "grad_norm", "completion_ids", "completion_mask", "advantages", "weights_sample",
+                        "grad_sample"}
+    assert all(a.dtype in (np.float32, np.float64) for a in got.values())
+    assert sum(a.nbytes for a in got.values()) <= 64 << 20
+    assert got["completion_ids"].shape == (64, 256) and got["advantages"].shape == (64,)
+    assert all(np.isfinite(a).all() for a in got.values())
+    assert np.abs(got["grad_sample"]).max() > 0 and got["grad_norm"][0] > 0
+
+
 def _rccl_worker(port, q):
     os.environ.update(RANK="0", WORLD_SIZE="1", LOCAL_RANK="0", MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
     try:

@@ -330,8 +330,8 @@ def test_ppo_two_update_bf16_trajectory_within_reference_bands(dev, width):
     print(width, "update, stat, product, oracle bf16, oracle fp32, band:", report)
 
 
-def test_ppo_trainer_train_runs(dev):
-    tr, _ = _trainer(dev)
+def test_ppo_trainer_train_runs(dev, tmp_path):
+    tr, _ = _trainer(dev, output_dir=str(tmp_path))  # the end-of-training checkpoint stays out of the tree
     before = tr.policy_model.flat.clone()
     vbefore = tr.value_model.flat.clone()
     state = tr.train()

@@ -6,7 +6,7 @@
 #   suite    pytest -m gpu (whole suite, one process) + smoke()      -> <tag>_gpu_suite.log
 #   sel      pytest -m gpu -k "$SEL" (a subset, one process)         -> <tag>_gpu_sel.log
 #   pmc      rocprofv3 FETCH_SIZE / WRITE_SIZE passes over tools/bench_decode.py -> <tag>_pmc_decode.json
-#   bench    python bench.py (default K / W, CPU baseline included)  -> <tag>_bench.json
+#   bench    python bench.py --full (default K / W, roofline + CPU baseline) -> <tag>_bench.json
 #   prof     rocprofv3 --kernel-trace --stats of bench.py --steps 1 --warmup 1 -> <tag>_bench_kernel_stats.csv
 #   decode   tools/bench_decode.py (per-kernel decode timings)       -> <tag>_decode.log
 #   train    tools/train_kernels.py (training half-step)             -> <tag>_train.log
@@ -46,7 +46,7 @@ for step in "$@"; do
         || fail pmc_summary $? /dev/null
       rm -rf $O/pmc_FETCH_SIZE $O/pmc_WRITE_SIZE ;;
     bench)
-      timeout -k 10 600 python -u bench.py > $O/${tag}_bench.json 2> $O/${tag}_bench.err \
+      timeout -k 10 600 python -u bench.py --full > $O/${tag}_bench.json 2> $O/${tag}_bench.err \
         || fail bench $? $O/${tag}_bench.err
       tail -c 400 $O/${tag}_bench.json ;;
     prof)
