@@ -74,6 +74,9 @@ typedef struct swh_launch_policy {
                             * 0 auto (the count that fills the CUs best), 6, 7, 8; 0 */
     int32_t attn_pair;     /* 1: decode attention at D = 128 on one workgroup per (kv head, two rows),
                             * a shared GRPO prompt's keys read once for both; 0: one per row; 1 */
+    int32_t tile_pipe;     /* 1: the tile kernel (gate/up, plain / bias tiles; K = 896 or 1024) runs a wave's
+                            * first-tile MFMAs of k 0..511 under the landing of the rest of the X image;
+                            * 0: it loads everything, then computes; 1 */
 } swh_launch_policy;
 int swh_launch_policy_default(swh_launch_policy *out);
 int swh_get_launch_policy(swh_launch_policy *out);

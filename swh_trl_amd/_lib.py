@@ -48,7 +48,8 @@ class LaunchPolicy(C.Structure):
     _fields_ = [("wide_kmin", c_i64), ("wide_gemm", c_i32), ("wide_smax", c_i32), ("wide_cb", c_i32),
                 ("gemm_ms", c_i32), ("gemm_cb", c_i32), ("gemm_s", c_i32), ("gemm_persist", c_i32),
                 ("gemm_wn", c_i32), ("gemm_tile", c_i32), ("gemm_nw", c_i32), ("xstream", c_i32),
-                ("lm_ring14", c_i32), ("filt_wgs", c_i32), ("wide_waves", c_i32), ("attn_pair", c_i32)]
+                ("lm_ring14", c_i32), ("filt_wgs", c_i32), ("wide_waves", c_i32), ("attn_pair", c_i32),
+                ("tile_pipe", c_i32)]
 
 
 # name -> (restype, argtypes)

@@ -69,6 +69,40 @@ __device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(
 
 __device__ __forceinline__ bf16x8 as_bf16x8(const uint4 &v) { return __builtin_bit_cast(bf16x8, v); }
 
+// Loads the compiler does not count (the pipelined tile prologue, lm_head_kernel PIPE):
+// beside an LDS-DMA in flight hipcc waits vmcnt(0) before the first use of any load it
+// can see, so the weight fragments and the A-fragment LDS reads are issued from asm
+// statements and retired by hand-counted waits.  A destination is valid only after the
+// wait statement that names it ("+v": the compiler cannot read or copy it earlier).
+__device__ __forceinline__ bf16x8 as_bf16x8(const u32x4 &v) { return __builtin_bit_cast(bf16x8, v); }
+template <bool NT>
+__device__ __forceinline__ void ldw_hidden(u32x4 &d, const uint16_t *p) {
+    if constexpr (NT) asm volatile("global_load_dwordx4 %0, %1, off nt" : "=v"(d) : "v"(p) : "memory");
+    else asm volatile("global_load_dwordx4 %0, %1, off" : "=v"(d) : "v"(p) : "memory");
+}
+template <int OFF>
+__device__ __forceinline__ void lds128_hidden(u32x4 &d, uint32_t base) {
+    static_assert(OFF >= 0 && OFF < 65536, "ds_read offset field");
+    asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(d) : "v"(base), "n"(OFF) : "memory");
+}
+template <int N>
+__device__ __forceinline__ void vm_wait() {
+    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
+}
+__device__ __forceinline__ void landed(u32x4 &d) { asm volatile("" : "+v"(d)); }  // after the wait that retires d
+// at most N LDS reads younger than these four are outstanding
+template <int N>
+__device__ __forceinline__ void lgkm_wait(u32x4 (&a)[4]) {
+    asm volatile("s_waitcnt lgkmcnt(%4)" : "+v"(a[0]), "+v"(a[1]), "+v"(a[2]), "+v"(a[3]) : "n"(N) : "memory");
+}
+template <int I, int N, class F>
+__device__ __forceinline__ void static_for(F &&f) {
+    if constexpr (I < N) {
+        f(std::integral_constant<int, I>{});
+        static_for<I + 1, N>(f);
+    }
+}
+
 // Normalised X: bf16(w * bf16(x * rstd)) for 8 consecutive k (Qwen2RMSNorm's
 // two roundings), packed f32 math: 4 VALU per element.
 typedef float f32x2 __attribute__((ext_vector_type(2)));
@@ -842,7 +876,10 @@ __device__ __forceinline__ float row16_sum(float v) {
 // scores (the drawn token's log-prob, swh_lm_head_sample_logp): per tile and row a
 // 16-lane max and sum of e^(z - max), folded into one running (max, sum) per lane —
 // lane rl owns row 16 (rl >> 2) + 4 g + (rl & 3) — so the state costs two registers
-template <int NM, int EPI, bool BIAS, int SAMPLE, int KSC, int RD = 0>
+// PIPE: the prologue and the first tile of every wave by K chunk (below); later tiles of a
+// wave and every epilogue are the PIPE = 0 code, and the arithmetic is the same MFMAs in the
+// same order, so the outputs are bit-identical (tests/test_tile_pipe_gpu.py)
+template <int NM, int EPI, bool BIAS, int SAMPLE, int KSC, int RD = 0, int PIPE = 0>
 __global__ __launch_bounds__(RD ? 768 : 512) void lm_head_kernel(const uint16_t *__restrict__ x, const uint16_t *__restrict__ w,
                                                       int M, int N, int K, const uint16_t *__restrict__ norm_w,
                                                       float eps, const float *__restrict__ ss_in,
@@ -882,13 +919,13 @@ __global__ __launch_bounds__(RD ? 768 : 512) void lm_head_kernel(const uint16_t 
         for (int ks = 0; ks < KR; ++ks)
             if (KSC || ks < KS) bv[ks] = ld_wt<EPI == EPI_SILU>(wr + ks * wst);
     };
-    if (t < ntile) issue(t);  // the weight stream first
+    if (PIPE == 0 && t < ntile) issue(t);  // the weight stream first
     // RMSNorm partials and norm weights (L2), then the X image by LDS-DMA
     const int nc = K / 64;
     // folded norm: 8 lanes per row sum the row's chunk partials in registers and the
     // row statistic is in LDS by the image barrier (no LDS pass, no extra barrier)
-    const bool reg_rstd = NM == 2 && ss_in && 64 * 8 <= NT && nc <= 64;
-    const bool use_ss = NM && ss_in && 64 * nc <= 4 * NT && !reg_rstd;
+    const bool reg_rstd = PIPE == 0 && NM == 2 && ss_in && 64 * 8 <= NT && nc <= 64;
+    const bool use_ss = PIPE == 0 && NM && ss_in && 64 * nc <= 4 * NT && !reg_rstd;
     float4 ssv[4];
     float4 ss8[8];
     uint4 nwv[2];
@@ -914,7 +951,7 @@ __global__ __launch_bounds__(RD ? 768 : 512) void lm_head_kernel(const uint16_t 
         }
     }
     const int ppr = K / 8, jpl = (ppr + 63) >> 6;
-    for (int r = wid; r < 64; r += NW) {
+    for (int r = PIPE ? 64 : wid; r < 64; r += NW) {
         const uint16_t *src = x + (int64_t)min(m0 + r, M - 1) * K;
         for (int j = 0; j < jpl; ++j) {
             const int c = lane + 64 * j;
@@ -941,8 +978,10 @@ __global__ __launch_bounds__(RD ? 768 : 512) void lm_head_kernel(const uint16_t 
                 reinterpret_cast<float4 *>(nw_s)[2 * (tid + q * NT) + 1] = float4{f[4], f[5], f[6], f[7]};
             }
     }
-    SWH_GEMM_TRACE(1);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // image (and this wave's first tile) landed
+    if constexpr (PIPE == 0) {
+        SWH_GEMM_TRACE(1);
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // image (and this wave's first tile) landed
+    }
     if (reg_rstd) {
         const int r = tid >> 3, sub = tid & 7;
         float v = 0.f;
@@ -954,9 +993,11 @@ __global__ __launch_bounds__(RD ? 768 : 512) void lm_head_kernel(const uint16_t 
         v += __shfl_xor(v, 4);
         if (r < 64 && sub == 0) rstd_s[r] = rsqrtf(v / (float)K + eps);
     }
-    lds_barrier();
-    SWH_GEMM_TRACE(2);
-    if (NM != 0 && !reg_rstd) {
+    if constexpr (PIPE == 0) {
+        lds_barrier();
+        SWH_GEMM_TRACE(2);
+    }
+    if (PIPE == 0 && NM != 0 && !reg_rstd) {
         if (tid < 64) {
             float ssum = 0.f;
             if (use_ss) {
@@ -972,6 +1013,110 @@ __global__ __launch_bounds__(RD ? 768 : 512) void lm_head_kernel(const uint16_t 
             rstd_s[tid] = rsqrtf(ssum / (float)K + eps);
         }
         lds_barrier();
+    }
+    // PIPE: the prologue and the wave's first tile by K chunk.  The j = 0 DMA of an image
+    // row covers k-steps 0-15 and the j = 1 DMA the rest, so a wave issues: weights of
+    // chunk 0, its 8 rows' j = 0 DMAs, weights of chunk 1, the j = 1 DMAs, the row
+    // statistics.  vmcnt retires in order: waiting until only the instructions issued
+    // after chunk 0 remain, then the barrier, proves chunk 0 of the image (every wave's
+    // share) and of this wave's weights in place, and its 64 MFMAs run under the landing of
+    // chunk 1.  Every wave executes the same barriers, with or without a tile.
+    f32x4 acc[4];
+    bool piped = false;  // the first tile's accumulators are already complete
+    if constexpr (PIPE != 0) {
+        static_assert(KSC > 16 && KSC <= 32 && RD == 0 && NM != 1 && SAMPLE == 0,
+                      "the pipelined prologue: compile-time K of two DMA runs per row, 8 waves, no image pass");
+        constexpr int KS0 = 16, KC = KSC * 32, RSC = KC * 2 + 16, PPR = KC / 8, NCC = KC / 64;
+        constexpr int NSS = NM == 2 ? 2 : 0;  // row-statistic loads per lane (NCC <= 16 float4 chunks over 8 lanes)
+        const bool own = __builtin_amdgcn_readfirstlane(t < ntile ? 1 : 0) != 0;
+        const uint16_t *wr = wbase(own ? t : 0);
+        u32x4 wv[KSC];
+        auto dma = [&](int j) __attribute__((always_inline)) {
+#pragma unroll
+            for (int q = 0; q < 8; ++q) {
+                const int r = wid + 8 * q, c = lane + 64 * j;
+                const uint16_t *src = x + (int64_t)min(m0 + r, M - 1) * KC;
+                if (c < PPR)
+                    __builtin_amdgcn_global_load_lds(src + c * 8,
+                                                     (__attribute__((address_space(3))) void *)(xs + r * RSC + j * 1024),
+                                                     16, 0, 0);
+            }
+        };
+        if (own) static_for<0, KS0>([&](auto k) __attribute__((always_inline)) {
+            ldw_hidden<EPI == EPI_SILU>(wv[decltype(k)::value], wr + decltype(k)::value * wst);
+        });
+        __builtin_amdgcn_sched_barrier(0);
+        dma(0);
+        __builtin_amdgcn_sched_barrier(0);
+        if (own) static_for<KS0, KSC>([&](auto k) __attribute__((always_inline)) {
+            ldw_hidden<EPI == EPI_SILU>(wv[decltype(k)::value], wr + decltype(k)::value * wst);
+        });
+        __builtin_amdgcn_sched_barrier(0);
+        dma(1);
+        __builtin_amdgcn_sched_barrier(0);
+        float4 st[2];
+        if constexpr (NM == 2) {
+            const float4 *row =
+                reinterpret_cast<const float4 *>(ss_in + (int64_t)min(m0 + (tid >> 3), M - 1) * (KC / 16));
+            st[0] = row[tid & 7];
+            st[1] = row[min((tid & 7) + 8, NCC - 1)];
+        }
+        __builtin_amdgcn_sched_barrier(0);
+        SWH_GEMM_TRACE(1);
+        // still in flight after chunk 0: chunk 1's weights (a wave with a tile), 8 DMAs, the statistics
+        if (own) vm_wait<KSC - KS0 + 8 + NSS>();
+        else vm_wait<8 + NSS>();
+        lds_barrier();
+        SWH_GEMM_TRACE(7);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) acc[i] = f32x4{0.f, 0.f, 0.f, 0.f};
+        // A fragments one k-step ahead, as the later tiles; rows 16 i of the image from two
+        // bases (the ds_read offset field is 16 bits)
+        const uint32_t xa0 = (uint32_t)(uintptr_t)(const __attribute__((address_space(3))) unsigned char *)(
+            xs + rl * RSC + kq * 2);
+        const uint32_t xa2 = xa0 + 32 * RSC;
+        u32x4 a[2][4];
+        auto read_a = [&](auto k, u32x4(&d)[4]) __attribute__((always_inline)) {
+            constexpr int ks = decltype(k)::value;
+            lds128_hidden<ks * 64>(d[0], xa0);
+            lds128_hidden<16 * RSC + ks * 64>(d[1], xa0);
+            lds128_hidden<ks * 64>(d[2], xa2);
+            lds128_hidden<16 * RSC + ks * 64>(d[3], xa2);
+        };
+        auto mma_chunk = [&](auto k0, auto k1) __attribute__((always_inline)) {
+            constexpr int K0 = decltype(k0)::value, K1 = decltype(k1)::value;
+            static_for<K0, K1>([&](auto k) __attribute__((always_inline)) { landed(wv[decltype(k)::value]); });
+            read_a(k0, a[K0 & 1]);
+            static_for<K0, K1>([&](auto k) __attribute__((always_inline)) {
+                constexpr int ks = decltype(k)::value;
+                if constexpr (ks + 1 < K1) read_a(std::integral_constant<int, ks + 1>{}, a[(ks + 1) & 1]);
+                lgkm_wait<(ks + 1 < K1) ? 4 : 0>(a[ks & 1]);
+                __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+                for (int i = 0; i < 4; ++i)
+                    acc[i] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(as_bf16x8(a[ks & 1][i]), as_bf16x8(wv[ks]), acc[i],
+                                                                    0, 0, 0);
+                __builtin_amdgcn_sched_barrier(0);
+            });
+        };
+        if (own) mma_chunk(std::integral_constant<int, 0>{}, std::integral_constant<int, KS0>{});
+        vm_wait<0>();  // chunk 1: everything this wave issued
+        lds_barrier();
+        SWH_GEMM_TRACE(2);
+        if (own) mma_chunk(std::integral_constant<int, KS0>{}, std::integral_constant<int, KSC>{});
+        piped = own;
+        if constexpr (NM == 2) {  // the row statistic, needed by the epilogue only
+            const int r = tid >> 3, sub = tid & 7;
+            float v = 0.f;
+#pragma unroll
+            for (int j = 0; j < 2; ++j)
+                if (sub + 8 * j < NCC) v += ((st[j].x + st[j].y) + st[j].z) + st[j].w;
+            v += __shfl_xor(v, 1);
+            v += __shfl_xor(v, 2);
+            v += __shfl_xor(v, 4);
+            if (sub == 0) rstd_s[r] = rsqrtf(v / (float)KC + eps);
+            lds_barrier();
+        }
     }
     SWH_GEMM_TRACE(3);
     float rsr[4][4];  // folded RMSNorm (NM 2): the row scale of each accumulator row
@@ -1021,16 +1166,23 @@ __global__ __launch_bounds__(RD ? 768 : 512) void lm_head_kernel(const uint16_t 
         temp = (!smp.p.greedy && smp.p.temperature != 1.0f) ? smp.p.temperature : 1.f;
     }
     for (; t < ntile; t += tstep) {
-        f32x4 acc[4];
+        // (PIPE: the first tile is accumulated; its successor's weights are issued whole,
+        // below, once no hidden load is in flight)
+        const bool mma = !(PIPE != 0 && piped);
+        piped = false;
+        if (mma) {
 #pragma unroll
-        for (int i = 0; i < 4; ++i) acc[i] = f32x4{0.f, 0.f, 0.f, 0.f};
+            for (int i = 0; i < 4; ++i) acc[i] = f32x4{0.f, 0.f, 0.f, 0.f};
+        }
         const unsigned char *xrow = xs + rl * RS + kq * 2;
         // ring refill: k-step ks's weight register takes the next tile's fragment as
         // soon as its MFMA has read it, so a wave always has KS loads in flight
-        const bool ring = SWH_LM_RING && KSC != 0 && t + tstep < ntile;
+        const bool ring = mma && SWH_LM_RING && KSC != 0 && t + tstep < ntile;
         const uint16_t *wnext = wbase(ring ? t + tstep : t);
         const uint16_t *wcur = wbase(t);
-        if constexpr (KSC != 0) {
+        if (!mma) {
+            // accumulated by the pipelined prologue
+        } else if constexpr (KSC != 0) {
             // A fragments double-buffered one k-step ahead (2 and 3 ahead measured no faster
             // for gate/up: 11.24 / 11.38-11.42 against 11.15-11.21 us, profiles/r5_gu_apf_ab.log);
             // the scheduling barrier keeps the compiler from hoisting every read
@@ -2185,13 +2337,13 @@ int launch_gemm_ms(const GemmCfg &c, dim3 grid, size_t lds, hipStream_t s, const
     }
 }
 
-template <int NM, int EPI, bool BIAS, int SAMPLE, int KSC, int RD = 0>
+template <int NM, int EPI, bool BIAS, int SAMPLE, int KSC, int RD = 0, int PIPE = 0>
 int launch_lm_ks(dim3 grid, size_t lds, hipStream_t s, const uint16_t *X, const uint16_t *W, int M, int N, int K,
                  const uint16_t *NWt, float eps, const float *ss_in, const uint16_t *Bs, uint16_t *Y, int ldy,
                  const LmSample &smp) {
-    if (!lds_opt_in<&lm_head_kernel<NM, EPI, BIAS, SAMPLE, KSC, RD>>()) return SWH_E_LAUNCH;  // > 64 KB LDS
-    lm_head_kernel<NM, EPI, BIAS, SAMPLE, KSC, RD><<<grid, RD ? 768 : 512, lds, s>>>(X, W, M, N, K, NWt, eps, ss_in, Bs,
-                                                                                  Y, ldy, smp);
+    if (!lds_opt_in<&lm_head_kernel<NM, EPI, BIAS, SAMPLE, KSC, RD, PIPE>>()) return SWH_E_LAUNCH;  // > 64 KB LDS
+    lm_head_kernel<NM, EPI, BIAS, SAMPLE, KSC, RD, PIPE><<<grid, RD ? 768 : 512, lds, s>>>(X, W, M, N, K, NWt, eps, ss_in,
+                                                                                        Bs, Y, ldy, smp);
     return launch_status();
 }
 
@@ -2199,6 +2351,16 @@ int launch_lm_ks(dim3 grid, size_t lds, hipStream_t s, const uint16_t *X, const 
 // (three per SIMD): 58.2-58.8 against 60.3-60.4 us per launch, bench +0.6 % (launch policy
 // lm_ring14 = 0: off; read per call)
 inline bool lm_ring14() { return launch_policy().lm_ring14 != 0; }
+
+// the pipelined prologue (lm_head_kernel PIPE): the first tile's MFMAs of k-steps 0-15 under
+// the landing of the rest of the X image (launch policy tile_pipe, read per call).  It has
+// no pass over the image, so it takes plain X or the folded norm with the row statistics
+// given; the fused sampler keeps the load-all prologue (its log-prob variants sit at
+// 251-253 VGPRs and the K = 896 sampler runs 12 waves, where a wave's image share differs).
+template <int NM, int SAMPLE>
+inline bool tile_pipe(const float *ss_in) {
+    return SAMPLE == 0 && (NM == 0 || (NM == 2 && ss_in)) && launch_policy().tile_pipe != 0;
+}
 
 // compile-time k-step counts for the model widths in use (Qwen2.5-0.5B: H = 896)
 template <int NM, int EPI, bool BIAS, int SAMPLE>
@@ -2214,8 +2376,19 @@ int launch_lm(dim3 grid, size_t lds, hipStream_t s, const uint16_t *X, const uin
         if ((SAMPLE == 1 || SAMPLE == 2) && lm_ring14())  // (the log-prob variants spill at 768 threads)
             return launch_lm_ks<NM, EPI, BIAS, SAMPLE, 28, 14>(grid, lds, s, X, W, M, N, K, NWt, eps, ss_in, Bs, Y, ldy,
                                                                smp);
+        if constexpr (SAMPLE == 0 && NM != 1) {
+            if (tile_pipe<NM, SAMPLE>(ss_in))
+                return launch_lm_ks<NM, EPI, BIAS, SAMPLE, 28, 0, 1>(grid, lds, s, X, W, M, N, K, NWt, eps, ss_in, Bs, Y,
+                                                                    ldy, smp);
+        }
         return launch_lm_ks<NM, EPI, BIAS, SAMPLE, 28>(grid, lds, s, X, W, M, N, K, NWt, eps, ss_in, Bs, Y, ldy, smp);
-    case 32: return launch_lm_ks<NM, EPI, BIAS, SAMPLE, 32>(grid, lds, s, X, W, M, N, K, NWt, eps, ss_in, Bs, Y, ldy, smp);
+    case 32:
+        if constexpr (SAMPLE == 0 && NM != 1) {
+            if (tile_pipe<NM, SAMPLE>(ss_in))
+                return launch_lm_ks<NM, EPI, BIAS, SAMPLE, 32, 0, 1>(grid, lds, s, X, W, M, N, K, NWt, eps, ss_in, Bs, Y,
+                                                                    ldy, smp);
+        }
+        return launch_lm_ks<NM, EPI, BIAS, SAMPLE, 32>(grid, lds, s, X, W, M, N, K, NWt, eps, ss_in, Bs, Y, ldy, smp);
     default: return launch_lm_ks<NM, EPI, BIAS, SAMPLE, 0>(grid, lds, s, X, W, M, N, K, NWt, eps, ss_in, Bs, Y, ldy, smp);
     }
 }

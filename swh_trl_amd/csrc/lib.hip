@@ -36,6 +36,7 @@ swh_launch_policy default_policy() {
     p.lm_ring14 = 1;
     p.filt_wgs = 1024;
     p.attn_pair = 1;
+    p.tile_pipe = 1;
     return p;
 }
 // each host thread holds its own policy (the defaults until it sets one), so two
@@ -77,7 +78,7 @@ extern "C" int swh_set_launch_policy(const swh_launch_policy *p) {
                      !in(p->gemm_wn, {1, 2, 4}))) ||
         !in(p->gemm_tile, {0, 1}) || !in(p->gemm_nw, {0, 4, 8, 16}) || !in(p->xstream, {0, 1}) ||
         !in(p->lm_ring14, {0, 1}) || p->filt_wgs < 64 || p->filt_wgs > 65536 || !in(p->wide_waves, {0, 6, 7, 8}) ||
-        !in(p->attn_pair, {0, 1}))
+        !in(p->attn_pair, {0, 1}) || !in(p->tile_pipe, {0, 1}))
         return SWH_E_ARG;
     t_policy = *p;
     return SWH_OK;

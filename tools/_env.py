@@ -5,7 +5,7 @@ into the product's explicit configuration (the product reads no environment).
     SWH_TRACE=1                   phase timings on stderr (profiling.set_trace)
     SWH_GEMM_TUNING=use|tune|off  with SWH_GEMM_TABLE=<csv> (gemm_tuning.enable)
     SWH_WIDE_KMIN, SWH_WIDE_GEMM, SWH_WIDE_SMAX, SWH_WIDE_CB, SWH_GEMM_NW, SWH_XSTREAM,
-    SWH_LM_RING14, SWH_FILT_WGS, SWH_WIDE_WAVES, SWH_ATTN_PAIR, SWH_GEMM_CFG
+    SWH_LM_RING14, SWH_FILT_WGS, SWH_WIDE_WAVES, SWH_ATTN_PAIR, SWH_TILE_PIPE, SWH_GEMM_CFG
                                   the launch policy of the calling thread
     SWH_DECODE_GRAPH, SWH_DECODE_GRAPH_STEPS, SWH_DECODE_FUSED, SWH_DECODE_FOLD, SWH_WIDE_PACK,
     SWH_FRAGW, SWH_ACT_FRAG, SWH_ATT_FRAG, SWH_DECODE_SHARED_KV, SWH_PREFILL_DEDUP,
@@ -28,7 +28,7 @@ if ROOT not in sys.path:
 _POLICY = {"SWH_WIDE_KMIN": "wide_kmin", "SWH_WIDE_GEMM": "wide_gemm", "SWH_WIDE_SMAX": "wide_smax",
            "SWH_WIDE_CB": "wide_cb", "SWH_GEMM_NW": "gemm_nw", "SWH_XSTREAM": "xstream",
            "SWH_LM_RING14": "lm_ring14", "SWH_FILT_WGS": "filt_wgs", "SWH_WIDE_WAVES": "wide_waves",
-           "SWH_ATTN_PAIR": "attn_pair"}
+           "SWH_ATTN_PAIR": "attn_pair", "SWH_TILE_PIPE": "tile_pipe"}
 
 _BOOL = {"SWH_DECODE_GRAPH": "decode_graph", "SWH_DECODE_FUSED": "fused", "SWH_DECODE_FOLD": "fold_norm",
          "SWH_WIDE_PACK": "wide_pack", "SWH_FRAGW": "fragw", "SWH_ACT_FRAG": "act_frag", "SWH_ATT_FRAG": "att_frag",

@@ -1,8 +1,11 @@
 """Phase timing of the decode GEMM from inside the kernel (wall clock, 10 ns):
 per workgroup, wave 0 stamps entry, loads issued, statistic ready, MFMAs done,
 merged, split-K reduced, exit.  Builds tools/_build/libgemm_probe.so if absent.
+The tile kernel's pipelined prologue (launch policy tile_pipe) adds "c0": the
+barrier after the first K chunk of the X image, where its MFMAs start (p2 is
+then the barrier after the rest of the image, p3 the row statistic's).
 
-    python tools/gemm_probe.py [--cfg cb,nw,s]
+    python tools/gemm_probe.py [--cfg cb,nw,s] [--tile-pipe 0|1]
 """
 import argparse
 import ctypes
@@ -14,7 +17,7 @@ import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SO = os.environ.get("SWH_PROBE_SO", os.path.join(ROOT, "tools", "_probe", "libgemm_probe.so"))
-PHASES = ["p1", "p2", "p3", "p4", "p5", "exit"]
+PHASES = [(1, "p1"), (7, "c0"), (2, "p2"), (3, "p3"), (4, "p4"), (5, "p5"), (6, "exit")]  # (stamp slot, name), in time order
 
 
 def build():
@@ -30,9 +33,17 @@ def build():
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--cfg", default=None)
+    ap.add_argument("--tile-pipe", type=int, default=None, choices=(0, 1))
     args = ap.parse_args()
     build()
     lib = ctypes.CDLL(SO)
+    if args.tile_pipe is not None:
+        sys.path.insert(0, ROOT)
+        from swh_trl_amd import _lib as L
+        pol = L.LaunchPolicy()
+        lib.swh_get_launch_policy(ctypes.byref(pol))
+        pol.tile_pipe = args.tile_pipe
+        assert lib.swh_set_launch_policy(ctypes.byref(pol)) == 0
     if args.cfg:  # the probe library's own launch policy (the library reads no environment)
         sys.path.insert(0, ROOT)
         from swh_trl_amd import _lib as L
@@ -99,11 +110,11 @@ def main():
             continue
         entry = t[:, 0]
         t0 = int(entry.min())
-        span = (int(t[:, 1:7].max()) - t0) / 100.0
+        span = (int(t[:, 1:8].max()) - t0) / 100.0
         print(f"{name:8s} WGs={t.shape[0]:5d} event={1000 * e0.elapsed_time(e1):7.2f}us span={span:7.2f}us "
               f"entry spread p50={float((entry - t0).float().median()) / 100:6.2f} max={float(entry.max() - t0) / 100:6.2f}")
         prev = entry
-        for i, ph in enumerate(PHASES, start=1):
+        for i, ph in PHASES:
             col = t[:, i]
             ok = col > 0
             if not bool(ok.any()):
