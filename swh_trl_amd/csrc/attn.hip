@@ -7,7 +7,7 @@
 // 86-96): at the GRPO shape (64 sequences x 14/2 heads x 384 positions x 64)
 // aotriton's flash kernels run ~150 us forward / ~430 us backward per layer.
 //
-// Orientation (the decode kernel's, csrc/decode.hip attn_decode_kernel): one
+// Orientation (the decode kernel's, csrc/attn_decode.hip attn_decode_kernel): one
 // WAVE owns 16 queries and walks the keys in blocks of 32.  S^T = K Q^T on
 // v_mfma_f32_16x16x32_bf16 with the 16 queries as the MFMA columns, so each
 // lane holds one query and 8 keys: the softmax statistics need two lane
@@ -145,7 +145,7 @@ __device__ __forceinline__ void fa_load_rows(u32x4 (&r)[2][D / 32], const uint16
 // O^T[d][n] += X^T[d][rows of the block] Y^T[rows][n] where the block's 32 rows
 // X [32][D] are parked in the wave's LDS tile and Y^T comes as 8 fp32 values per
 // lane (rows 4g..4g+3 of the block's first 16, then of its second 16, column c16):
-// the decode kernel's P V step (csrc/decode.hip)
+// the decode kernel's P V step (csrc/attn_decode.hip)
 template <int D, int VS>
 __device__ __forceinline__ void fa_xty(f32x4a (&o)[D / 16], uint16_t *tile, const u32x4 (&x)[2][D / 32],
                                        const float (&y)[8], int c16, int g) {

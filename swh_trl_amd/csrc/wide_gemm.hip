@@ -19,20 +19,9 @@
 // partial sums ss_out), SiLU gate.
 #include <cstdlib>
 
-#include "common.hpp"
+#include "decode_common.hpp"  // this file's host functions as the decode sources see them; kCounterBytes
 
 namespace swh {
-
-int wide_gemm(const void *x, const void *w, int64_t M, int64_t N, int64_t K, float eps, const float *ss_in,
-              const void *bias, void *residual, int32_t silu, void *y, int64_t ldy, float *ss_out, void *workspace,
-              int64_t workspace_bytes, int64_t counter_bytes, int32_t packed, hipStream_t stream);
-int64_t wide_gemm_slab_bytes(int64_t M, int64_t N, int64_t K, int32_t silu);
-bool wide_gemm_eligible(int64_t M, int64_t N, int64_t K, int32_t silu);
-int wide_pack(const void *src, const void *norm_w, int64_t N, int64_t K, int32_t silu, void *dst, hipStream_t stream);
-int wide_lm_sample(const void *x, const void *w, int64_t M, int64_t V, int64_t K, float eps, const float *ss_in,
-                   const swh_sample_params &p, const uint64_t *rng, const int32_t *step, LmPart *part, int *pstride,
-                   hipStream_t stream);
-
 namespace {
 
 typedef __bf16 bf16x8w __attribute__((ext_vector_type(8)));
@@ -689,3 +678,41 @@ extern "C" int swh_wide_probe_set_trace(unsigned long long *p) {
 #endif
 
 }  // namespace swh
+
+using namespace swh;
+
+// Packed-weight form of the bandwidth-regime decode GEMM (csrc/wide_gemm.hip): w is the
+// fragment order swh_wide_pack writes.  Same arguments and epilogues as swh_decode_gemm
+// with a folded (or no) norm; shapes wide_gemm does not serve are SWH_E_ARG (no fallback:
+// the packed weight has no row-major reading).
+extern "C" int swh_wide_gemm_packed(const void *x, const void *w, int64_t M, int64_t N, int64_t K, float eps,
+                                    const void *bias, void *residual, int32_t silu, void *y, int64_t ldy,
+                                    const float *ss_in, float *ss_out, void *workspace, int64_t workspace_bytes,
+                                    void *stream) {
+    if (!x || !w || !wide_gemm_eligible(M, N, K, silu)) return SWH_E_ARG;
+    if (residual && (silu || bias || ss_in)) return SWH_E_ARG;
+    if (!residual && !y) return SWH_E_ARG;
+    if (ss_out && !residual) return SWH_E_ARG;
+    if (ldy % 8 || ldy < N) return SWH_E_ARG;
+    const uintptr_t out_ptr = reinterpret_cast<uintptr_t>(residual ? residual : y);
+    if ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(w) | out_ptr) & 15) return SWH_E_ARG;
+    if ((bias && (reinterpret_cast<uintptr_t>(bias) & 15)) || (ss_in && (reinterpret_cast<uintptr_t>(ss_in) & 15)))
+        return SWH_E_ARG;
+    const int st = wide_gemm(x, w, M, N, K, eps, ss_in, bias, residual, silu, y, ldy, ss_out, workspace,
+                             workspace_bytes, kCounterBytes, 1, static_cast<hipStream_t>(stream));
+    return st == 1 ? SWH_E_ARG : st;
+}
+
+// 1 when swh_wide_gemm_packed serves [M rows] x [N (x2 with silu), K].
+extern "C" int swh_wide_gemm_eligible(int64_t M, int64_t N, int64_t K, int32_t silu) {
+    return wide_gemm_eligible(M, N, K, silu) ? 1 : 0;
+}
+
+extern "C" int swh_wide_pack(const void *w, const void *norm_w, int64_t N, int64_t K, int32_t silu, void *dst,
+                             void *stream) {
+    if (!w || !dst || w == dst) return SWH_E_ARG;
+    if ((reinterpret_cast<uintptr_t>(w) | reinterpret_cast<uintptr_t>(dst) |
+         reinterpret_cast<uintptr_t>(norm_w)) & 15)
+        return SWH_E_ARG;
+    return wide_pack(w, norm_w, N, K, silu, dst, static_cast<hipStream_t>(stream));
+}

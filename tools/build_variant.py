@@ -1,7 +1,7 @@
 """Build an A/B variant of libswh_trl_amd.so with extra hipcc defines into
 tools/_build/<name>.so (load it with SWH_LIB_PATH=...).  Tuning aid only.
 
-    python tools/build_variant.py NAME [--only attn.hip,...] -DSWH_KU=16 [...]
+    python tools/build_variant.py NAME [--only wide_gemm.hip,...] -DSWH_WIDE_TRACE_ON [...]
 
 --only: recompile just those sources with the defines; the others are linked
 from the main build's objects (swh_trl_amd/_build, current after build()).
