@@ -679,6 +679,46 @@ int swh_layernorm_bwd(const void *s, const void *w, const float *mean, const flo
 int swh_gelu_tanh_fwd(const void *x, int64_t n, void *y, int32_t dtype, void *stream);
 int swh_gelu_tanh_bwd(const void *x, const void *dy, int64_t n, void *dx, int32_t dtype, void *stream);
 
+/* ---- LoRA adapters (csrc/lora.hip) -------------------------------------------
+ * The rank-r path of a peft LoRA Linear, y = x W^T + s (x A^T) B^T with W frozen
+ * (the only training mode of the reference: trl/trainer/grpo_trainer.py:653-699
+ * forces LoraConfig(r=16, lora_alpha=32) whenever peft_config is given; the
+ * adapter is merged into W for generation, :1335-1378).  For W [N, K] the
+ * adapter is A [Rp, K] and Bt [Rp, N] (B transposed), row-major, Rp = r rounded
+ * up to 16 with zero pad rows, so the four entries below serve the forward, the
+ * input gradient and both weight gradients without a transpose.  bf16 operands
+ * (dtype SWH_BF16; anything else SWH_E_DTYPE), fp32 accumulation, no atomics
+ * (bit-identical reruns).  1 <= r <= 64, 16-B aligned bases, leading dimensions
+ * multiples of 8 elements and >= the row width; else SWH_E_ARG.
+ *
+ * swh_lora_down: u[T, Rp] (bf16) = x[T, K] M[Rp, K]^T, K % 32 == 0; columns >= r
+ * of u are written as zero.  u = x A^T forward, v = dy B backward (M = Bt). */
+int swh_lora_down(const void *x, const void *M, void *u, int64_t T, int64_t K, int32_t r, int64_t ldx, int64_t ldm,
+                  int64_t ldu, int32_t dtype, void *stream);
+/* swh_lora_up_add: y[T, C] = bf16(y + scale u[T, Rp] M[Rp, C]) in place, C % 16 ==
+ * 0: the product and the sum in fp32, one rounding; an element whose update is
+ * zero keeps its bits; nothing outside the [T, C] window is touched.
+ * y += s u Bt forward, dx += s v A backward. */
+int swh_lora_up_add(const void *u, const void *M, void *y, int64_t T, int64_t C, int32_t r, int64_t ldu, int64_t ldm,
+                    int64_t ldy, float scale, int32_t dtype, void *stream);
+/* swh_lora_grad: G[r, C] (fp32, row stride ldg % 4 == 0) += scale u[T, Rp]^T in[T, C],
+ * C % 16 == 0: fp32 partials over fixed 1024-token chunks (each summed in token
+ * order) in `workspace` (>= swh_lora_grad_workspace_bytes, 16-B aligned), folded
+ * in chunk order.  Rows >= r of G are not touched.  dA (u = v, in = x) and dBt
+ * (u = u, in = dy); dtype describes u and in. */
+int64_t swh_lora_grad_workspace_bytes(int64_t T, int64_t C, int32_t r);
+int swh_lora_grad(const void *u, const void *in, float *G, int64_t T, int64_t C, int32_t r, int64_t ldu, int64_t ldin,
+                  int64_t ldg, float scale, int32_t dtype, void *workspace, int64_t workspace_bytes, void *stream);
+/* swh_lora_merge: out_j[N, K] = bf16(W_j + scale_j Bt_j^T A_j) (fp32 sum, one
+ * rounding; where the update is zero the output bits are W's) for every job of
+ * the device-resident table jobs[njobs] = {W, A, Bt, out (bf16, contiguous:
+ * W / out [N, K], A [Rp, K], Bt [Rp, N]), int64 N, K, r, tile0, double scale}:
+ * tile0 is the prefix sum of swh_lora_merge_tiles(N, K) over the jobs before,
+ * total_tiles the sum over all; K % 16 == 0, njobs <= 256.  One launch merges
+ * every target matrix of a model (the generator-sync merge, :1335-1378). */
+int64_t swh_lora_merge_tiles(int64_t N, int64_t K);
+int swh_lora_merge(const void *jobs, int32_t njobs, int64_t total_tiles, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

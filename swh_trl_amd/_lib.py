@@ -157,6 +157,13 @@ SIGNATURES = {
                                      c_vp, c_vp, c_i64, c_vp]),
     "swh_attn_decode_l3": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i32, c_i32, c_i32, c_i32,
                                    c_f32, c_vp, c_i32, c_vp, c_i32, c_i32, c_vp, c_vp]),
+    "swh_lora_down": (c_i32, [c_vp, c_vp, c_vp, c_i64, c_i64, c_i32, c_i64, c_i64, c_i64, c_i32, c_vp]),
+    "swh_lora_up_add": (c_i32, [c_vp, c_vp, c_vp, c_i64, c_i64, c_i32, c_i64, c_i64, c_i64, c_f32, c_i32, c_vp]),
+    "swh_lora_grad_workspace_bytes": (c_i64, [c_i64, c_i64, c_i32]),
+    "swh_lora_grad": (c_i32, [c_vp, c_vp, c_vp, c_i64, c_i64, c_i32, c_i64, c_i64, c_i64, c_f32, c_i32, c_vp, c_i64,
+                              c_vp]),
+    "swh_lora_merge_tiles": (c_i64, [c_i64, c_i64]),
+    "swh_lora_merge": (c_i32, [c_vp, c_i32, c_i64, c_vp]),
 }
 
 _lib = None

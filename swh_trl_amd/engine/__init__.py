@@ -4,6 +4,7 @@ import torch
 from .config import DecoderConfig, llama3_8b, qwen2_5_0_5b, tiny_llama, tiny_qwen2
 from .decode import DecodeEngine
 from .gpt2 import GPT2DecodeEngine, GPT2LM, gpt2_config
+from .lora import LoraCausalLM, LoraConfig
 from .model import CausalLM
 from .ref_decode import RefDecodeEngine
 
@@ -23,6 +24,6 @@ def build_engine(model: CausalLM, batch_size: int, max_prompt_len: int, max_new_
     return DecodeEngine(model, batch_size, max_prompt_len, max_new_tokens, **kw)
 
 
-__all__ = ["DecoderConfig", "CausalLM", "DecodeEngine", "RefDecodeEngine", "GPT2LM", "GPT2DecodeEngine", "build_model",
+__all__ = ["DecoderConfig", "CausalLM", "LoraCausalLM", "LoraConfig", "DecodeEngine", "RefDecodeEngine", "GPT2LM", "GPT2DecodeEngine", "build_model",
            "build_engine",
            "gpt2_config", "qwen2_5_0_5b", "llama3_8b", "tiny_qwen2", "tiny_llama"]

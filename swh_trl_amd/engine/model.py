@@ -627,6 +627,12 @@ class CausalLM:
     def _gv(self, name):
         return self.g.get(name) if self.grad is not None else None
 
+    def _proj(self, name: str, x: torch.Tensor) -> torch.Tensor:
+        """The decoder-layer Linear whose weight is self.p[name] (bias `..._b` where the
+        layout has one) on x.  engine/lora.py's LoraCausalLM adds the adapter path here."""
+        bn = name[:-2] + "_b"
+        return _Linear.apply(x, self.p[name], self.p.get(bn), self._gv(name), self._gv(bn), self.options)
+
     def _layer(self, i: int, x: torch.Tensor, h: torch.Tensor, positions, cos_t, sin_t, mask, kv_out=None):
         """Layer i on the residual stream x with h = RMSNorm_in(x) already formed;
         returns (x + attention, the MLP output d): the caller folds x + d into
@@ -634,8 +640,7 @@ class CausalLM:
         c = self.cfg
         B, L, _ = x.shape
         Hq, Hkv, D = c.num_attention_heads, c.num_key_value_heads, c.head_dim
-        qkv = _Linear.apply(h, self.p[f"l{i}.qkv_w"], self.p.get(f"l{i}.qkv_b"), self._gv(f"l{i}.qkv_w"),
-                            self._gv(f"l{i}.qkv_b"), self.options)
+        qkv = self._proj(f"l{i}.qkv_w", h)
         # split + rotate-half RoPE + [B, H, L, D] layout in one kernel each way
         q, k, v = nn_ops.QKVRopeFn.apply(qkv, positions, cos_t, sin_t, Hq, Hkv, D)
         if kv_out is not None:
@@ -662,11 +667,11 @@ class CausalLM:
     def _post_attention(self, i, x, o):
         """o-proj, residual + post-attention norm, the SiLU-gated MLP: (x + o, MLP output)."""
         c = self.cfg
-        o = _Linear.apply(o, self.p[f"l{i}.o_w"], None, self._gv(f"l{i}.o_w"), None, self.options)
+        o = self._proj(f"l{i}.o_w", o)
         x, h = _AddRMSNorm.apply(x, o, self.p[f"l{i}.ln_post"], self._gv(f"l{i}.ln_post"), c.rms_norm_eps)
-        gu = _Linear.apply(h, self.p[f"l{i}.gu_w"], None, self._gv(f"l{i}.gu_w"), None, self.options)
+        gu = self._proj(f"l{i}.gu_w", h)
         a = nn_ops.SiluMulFn.apply(gu)
-        d = _Linear.apply(a, self.p[f"l{i}.down_w"], None, self._gv(f"l{i}.down_w"), None, self.options)
+        d = self._proj(f"l{i}.down_w", a)
         return x, d
 
     def _mask(self, key_mask, L: int, padded: bool, device):
@@ -735,8 +740,7 @@ class CausalLM:
                 h = _RMSNorm.apply(x, self.p[f"l{i}.ln_in"], self._gv(f"l{i}.ln_in"), eps)
             else:
                 x, h = _AddRMSNorm.apply(x, d, self.p[f"l{i}.ln_in"], self._gv(f"l{i}.ln_in"), eps)
-            qkv = _Linear.apply(h, self.p[f"l{i}.qkv_w"], self.p.get(f"l{i}.qkv_b"), self._gv(f"l{i}.qkv_w"),
-                                self._gv(f"l{i}.qkv_b"), self.options)
+            qkv = self._proj(f"l{i}.qkv_w", h)
             if self._hip_attn:
                 # one node for both segments' RoPE; the attention reads the group's prompt
                 # Q/K/V in place and writes the token-major o_proj input (no cat / copies)

@@ -49,6 +49,7 @@ class EngineOptions:
     tgemm: str = "wgrad"             # csrc/tgemm.hip for narrow projections: off | wgrad | all (§14c)
     tgemm_splits: int = 8            # token splits of the gemm_tn weight gradient
     logp_chunk: int = 4096           # rows per fused lm-head log-prob chunk
+    hip_lora: bool = True            # csrc/lora.hip for the bf16 adapter path (else a torch composition)
 
     def __post_init__(self):
         if self.tgemm not in TGEMM_MODES:

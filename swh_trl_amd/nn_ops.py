@@ -747,3 +747,105 @@ class QKVRopeFn(torch.autograd.Function):
         call("swh_qkv_rope", dqkv.data_ptr(), pos.data_ptr(), cos.data_ptr(), sin.data_ptr(), B, L, Hq, Hkv, D,
              dq.data_ptr(), dk.data_ptr(), dv.data_ptr(), 1, _dtype_code(dq, "qkv_rope"), _stream())
         return dqkv, None, None, None, None, None, None
+
+
+# ---- LoRA adapter kernels (include/swh_trl_amd.h, csrc/lora.hip) ----------------------------------
+# Storage: for a Linear W [N, K] the adapter is A [Rp, K] and Bt [Rp, N] (B transposed), Rp = the
+# rank rounded up to 16 with zero pad rows.  All operands are bf16 2-D views with unit inner stride.
+
+def lora_rank_pad(r: int) -> int:
+    """Rows the rank-r adapter matrices are stored with."""
+    return (int(r) + 15) // 16 * 16
+
+
+def _lora_view_ok(t: torch.Tensor, dtype=torch.bfloat16) -> bool:
+    return (t.dim() == 2 and t.dtype == dtype and t.stride(1) == 1 and t.stride(0) % 8 == 0
+            and t.stride(0) >= t.shape[1] and t.data_ptr() % 16 == 0)
+
+
+def lora_eligible(x: torch.Tensor, m: torch.Tensor, r: int) -> bool:
+    """Operands the LoRA kernels take: bf16 views with unit inner stride, row
+    strides multiples of 8, 16-B aligned, 1 <= r <= 64, m [Rp, *]."""
+    return (1 <= r <= 64 and _lora_view_ok(x) and _lora_view_ok(m) and m.shape[0] == lora_rank_pad(r)
+            and x.device == m.device)
+
+
+def lora_down(x: torch.Tensor, m: torch.Tensor, r: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """u [T, Rp] = x [T, K] m [Rp, K]^T (swh_lora_down); columns >= r of u are zero."""
+    _dev(x, "lora_down")
+    if not lora_eligible(x, m, r) or x.shape[1] != m.shape[1] or x.shape[1] % 32:
+        raise ValueError(f"lora_down: unsupported operands {tuple(x.shape)} / {tuple(m.shape)} (r = {r})")
+    T, K = x.shape
+    Rp = m.shape[0]
+    if out is None:
+        out = torch.empty(T, Rp, device=x.device, dtype=x.dtype)
+    if not _lora_view_ok(out) or tuple(out.shape) != (T, Rp):
+        raise ValueError("lora_down: out must be a bf16 [T, Rp] view")
+    call("swh_lora_down", x.data_ptr(), m.data_ptr(), out.data_ptr(), T, K, int(r), x.stride(0), m.stride(0),
+         out.stride(0), _dtype_code(x, "lora_down"), _stream())
+    return out
+
+
+def lora_up_add(y: torch.Tensor, u: torch.Tensor, m: torch.Tensor, r: int, scale: float) -> torch.Tensor:
+    """y [T, C] += scale u [T, Rp] m [Rp, C] in place, fp32 sum and one rounding
+    (swh_lora_up_add); y may be a column window of a wider buffer."""
+    _dev(y, "lora_up_add")
+    if not (lora_eligible(u, m, r) and _lora_view_ok(y)) or u.shape[1] != m.shape[0] \
+            or tuple(y.shape) != (u.shape[0], m.shape[1]) or y.shape[1] % 16:
+        raise ValueError(f"lora_up_add: unsupported operands y {tuple(y.shape)} u {tuple(u.shape)} m {tuple(m.shape)}")
+    call("swh_lora_up_add", u.data_ptr(), m.data_ptr(), y.data_ptr(), y.shape[0], y.shape[1], int(r), u.stride(0),
+         m.stride(0), y.stride(0), float(scale), _dtype_code(y, "lora_up_add"), _stream())
+    return y
+
+
+def lora_grad(G: torch.Tensor, u: torch.Tensor, x: torch.Tensor, r: int, scale: float) -> torch.Tensor:
+    """G [Rp, C] (fp32) += scale u [T, Rp]^T x [T, C] over fixed token chunks folded
+    in order (swh_lora_grad: no atomics); rows >= r of G are not touched.  Returns
+    the workspace (keep it alive until the stream has run the launches)."""
+    _dev(x, "lora_grad")
+    Rp = lora_rank_pad(r)
+    ok = (1 <= r <= 64 and _lora_view_ok(u) and _lora_view_ok(x) and u.shape[0] == x.shape[0] and u.shape[1] == Rp
+          and x.shape[1] % 16 == 0 and G.dtype == torch.float32 and G.dim() == 2
+          and tuple(G.shape) == (Rp, x.shape[1]) and G.stride(1) == 1 and G.stride(0) % 4 == 0
+          and G.data_ptr() % 16 == 0)
+    if not ok:
+        raise ValueError(f"lora_grad: unsupported operands G {tuple(G.shape)} u {tuple(u.shape)} x {tuple(x.shape)}")
+    T, C = x.shape
+    need = _lib.load().swh_lora_grad_workspace_bytes(T, C, int(r))
+    ws = torch.empty(max(need, 16), device=x.device, dtype=torch.uint8)
+    call("swh_lora_grad", u.data_ptr(), x.data_ptr(), G.data_ptr(), T, C, int(r), u.stride(0), x.stride(0),
+         G.stride(0), float(scale), _dtype_code(x, "lora_grad"), ws.data_ptr(), ws.numel(), _stream())
+    return ws
+
+
+LORA_MERGE_MAX_JOBS = 256
+
+
+def lora_merge_table(jobs, device) -> tuple:
+    """The device job table of swh_lora_merge: jobs = [(W [N, K], A [Rp, K], Bt [Rp, N],
+    out [N, K], r, scale)], every tensor bf16 and contiguous.  Returns (table, njobs,
+    total_tiles); build it once, the pointers stay valid while the tensors live."""
+    import struct
+    lib = _lib.load()
+    if not 0 < len(jobs) <= LORA_MERGE_MAX_JOBS:
+        raise ValueError(f"lora_merge: 1..{LORA_MERGE_MAX_JOBS} jobs per table")
+    rows, tiles = [], 0
+    for (w, a, bt, out, r, scale) in jobs:
+        N, K = w.shape
+        Rp = lora_rank_pad(r)
+        ok = (1 <= r <= 64 and K % 16 == 0 and tuple(a.shape) == (Rp, K) and tuple(bt.shape) == (Rp, N)
+              and tuple(out.shape) == (N, K)
+              and all(t.dtype == torch.bfloat16 and t.is_contiguous() and t.is_cuda and t.data_ptr() % 16 == 0
+                      for t in (w, a, bt, out)))
+        if not ok:
+            raise ValueError(f"lora_merge: unsupported job W {tuple(w.shape)} A {tuple(a.shape)} Bt {tuple(bt.shape)}")
+        rows.append([w.data_ptr(), a.data_ptr(), bt.data_ptr(), out.data_ptr(), N, K, int(r), tiles,
+                     struct.unpack("q", struct.pack("d", float(scale)))[0]])
+        tiles += lib.swh_lora_merge_tiles(N, K)
+    return torch.tensor(rows, dtype=torch.int64).to(device), len(jobs), tiles
+
+
+def lora_merge(table: torch.Tensor, njobs: int, total_tiles: int) -> None:
+    """out_j = bf16(W_j + scale_j Bt_j^T A_j) for every job of a lora_merge_table, one launch."""
+    _dev(table, "lora_merge")
+    call("swh_lora_merge", table.data_ptr(), int(njobs), int(total_tiles), _stream())

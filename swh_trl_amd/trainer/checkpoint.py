@@ -83,15 +83,16 @@ def hf_config_dict(cfg: DecoderConfig, head: str = "lm", dtype: torch.dtype = to
     return d
 
 
-def _state_for_save(model: CausalLM) -> dict:
-    sd = model.hf_state_dict()
+def _state_for_save(model: CausalLM, sd: Optional[dict] = None) -> dict:
+    sd = dict(sd) if sd is not None else model.hf_state_dict()
     if model.cfg.tie_word_embeddings and model.head == "lm":
         sd.pop("lm_head.weight", None)  # tied to the embedding: transformers drops it on save
     return sd
 
 
-def save_pretrained(model: CausalLM, out_dir: str, eos_token_id=None, pad_token_id=None) -> None:
-    """Write `model` so transformers' from_pretrained (and `load_model`) reads it."""
+def save_pretrained(model: CausalLM, out_dir: str, eos_token_id=None, pad_token_id=None, state_dict=None) -> None:
+    """Write `model` so transformers' from_pretrained (and `load_model`) reads it.
+    state_dict: other weights under the transformers names (a LoRA model's merged weights)."""
     from safetensors.torch import save_file
     os.makedirs(out_dir, exist_ok=True)
     with open(os.path.join(out_dir, "config.json"), "w") as f:
@@ -99,7 +100,7 @@ def save_pretrained(model: CausalLM, out_dir: str, eos_token_id=None, pad_token_
     if model.head == "lm":
         with open(os.path.join(out_dir, "generation_config.json"), "w") as f:
             json.dump({"eos_token_id": eos_token_id, "pad_token_id": pad_token_id, "bos_token_id": None}, f, indent=2)
-    sd = _state_for_save(model)
+    sd = _state_for_save(model, state_dict)
     shards, cur, size = [], {}, 0
     for k, v in sd.items():  # in layout order; copies out of the flat buffer (no shared storage)
         nb = v.numel() * v.element_size()
@@ -269,9 +270,48 @@ def trainer_state_file(rank: int) -> str:
     return f"swh_trainer_state_{rank}.pt"
 
 
-def save_master(opt, out_dir: str) -> None:
+def save_master(opt, out_dir: str, moments: bool = False) -> None:
+    """The fp32 master weights; moments: also both AdamW moments (a LoRA run, whose
+    optimizer.pt has no transformers parameter list to follow)."""
     from safetensors.torch import save_file
-    save_file({"master": opt.master.detach().cpu().contiguous()}, os.path.join(out_dir, "swh_master.safetensors"))
+    sd = {"master": opt.master.detach().cpu().contiguous()}
+    if moments:
+        sd.update(exp_avg=opt.exp_avg.detach().cpu().contiguous(), exp_avg_sq=opt.exp_avg_sq.detach().cpu().contiguous(),
+                  step=torch.tensor(opt.step_count))
+    save_file(sd, os.path.join(out_dir, "swh_master.safetensors"))
+
+
+def save_adapter(model, out_dir: str, base_model_name_or_path: Optional[str] = None) -> None:
+    """peft's save_pretrained of a LoRA model: adapter_model.safetensors under peft's
+    key names (lora_A.weight [r, in], lora_B.weight [out, r]) and adapter_config.json."""
+    from safetensors.torch import save_file
+
+    from ..engine.lora import adapter_config_dict
+    os.makedirs(out_dir, exist_ok=True)
+    sd = {k: v.detach().cpu().contiguous() for k, v in model.adapter_state_dict().items()}
+    save_file(sd, os.path.join(out_dir, "adapter_model.safetensors"), metadata={"format": "pt"})
+    with open(os.path.join(out_dir, "adapter_config.json"), "w") as f:
+        json.dump(adapter_config_dict(model.spec, base_model_name_or_path), f, indent=2)
+
+
+def load_adapter_checkpoint(model, opt, ckpt_dir: str) -> None:
+    """Resume a LoRA run: the fp32 adapter master and moments where the checkpoint
+    holds them (exact), else the saved adapter weights as the master."""
+    from safetensors.torch import load_file
+    mp = os.path.join(ckpt_dir, "swh_master.safetensors")
+    if os.path.exists(mp):
+        sd = load_file(mp)
+        if sd["master"].numel() != opt.master.numel():
+            raise ValueError(f"{ckpt_dir}: the adapter master does not match this peft_config")
+        opt.master.copy_(sd["master"])
+        if "exp_avg" in sd:
+            opt.exp_avg.copy_(sd["exp_avg"])
+            opt.exp_avg_sq.copy_(sd["exp_avg_sq"])
+            opt.step_count = int(sd["step"])
+        model.adapter.copy_(opt.master)
+    else:
+        model.load_adapter_state_dict(load_file(os.path.join(ckpt_dir, "adapter_model.safetensors")))
+        opt.master.copy_(model.adapter.float())
 
 
 def load_weights_into(model: CausalLM, ckpt_dir: str) -> None:

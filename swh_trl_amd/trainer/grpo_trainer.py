@@ -12,6 +12,9 @@ per-token stage runs on the HIP engine:
   scoring      CausalLM forward -> lm head -> fused logp/entropy kernel
   loss         fused GRPO loss fwd+bwd kernel (all GA micro-batches in one pass)
   optimizer    flat-buffer AdamW + device grad-norm clip, RCCL all-reduce for DP
+  peft_config  LoRA adapters over the frozen base (:653-699; engine/lora.py): the optimizer and the
+               all-reduce cover the adapter only, the reference pass is the policy with its adapter
+               off (:1886), rollouts read the merged weights (:1335-1378)
 
 Fork-only additions of the reference (unsloth loading, CrossEncoder, private
 validation JSON, OpenAI client) are not part of the drop-in.
@@ -31,6 +34,7 @@ from .. import gemm_tuning
 from .. import ops
 from ..engine.config import DecoderConfig, PRESETS, from_hf_config
 from ..engine import build_engine, build_model
+from ..engine import lora as _lora
 from ..engine.gpt2 import warn_dropout
 from ..engine.decode import DecodeEngine
 from ..engine.model import CausalLM, dw_streams, dw_sync
@@ -281,8 +285,6 @@ class GRPOTrainer:
     def __init__(self, model, reward_funcs: Union[RewardFunc, list], args: Optional[GRPOConfig] = None,
                  train_dataset=None, eval_dataset=None, processing_class=None, reward_processing_classes=None,
                  callbacks=None, optimizers=(None, None), peft_config=None):
-        if peft_config is not None:
-            raise ValueError("peft_config: LoRA training is not part of the MI355X engine's scope")
         if optimizers is not None and any(o is not None for o in optimizers):
             raise ValueError("optimizers: the MI355X trainer updates its flat parameter buffer with the fused AdamW "
                              "kernel, configured by the GRPOConfig fields (learning_rate, adam_beta1/2, adam_epsilon, "
@@ -297,8 +299,22 @@ class GRPOTrainer:
         torch.cuda.set_device(self.device)
         gemm_tuning.enable()
         torch.manual_seed(a.seed)
-        self.model = load_model(model, self.device, trainable=True, seed=a.seed,
+        self.model = load_model(model, self.device, trainable=peft_config is None, seed=a.seed,
                                 dtype=None if hasattr(model, "parameters") else model_dtype(a.model_init_kwargs))
+        # peft_config: LoRA adapters over the frozen base (grpo_trainer.py:653-699), engine/lora.py
+        self.lora = self.model.spec if isinstance(self.model, _lora.LoraCausalLM) else None
+        self._base_name = None
+        if peft_config is not None:
+            self.lora = _lora.resolve(peft_config, self.model.cfg.model_type)
+            if a.sync_ref_model:
+                raise ValueError("sync_ref_model=True with peft_config: the reference policy is the base model under "
+                                 "the disabled adapter; there is no reference copy to mix the policy into")
+            if not isinstance(self.model, _lora.LoraCausalLM):
+                self.model = _lora.LoraCausalLM.from_base(self.model, self.lora, adapter_seed=a.seed)
+            elif self.model.spec != self.lora:
+                raise ValueError("peft_config does not match the LoraCausalLM's own adapter configuration")
+            self._base_name = model if isinstance(model, str) else getattr(getattr(model, "config", None),
+                                                                            "_name_or_path", None)
         self.processing_class = processing_class
         if not isinstance(reward_funcs, list):
             reward_funcs = [reward_funcs]
@@ -347,15 +363,16 @@ class GRPOTrainer:
             self.gen_pad_token_id = self.pad_token_id
         self.gen_kwargs = gen
         self.ref_model = None
-        if self.beta != 0.0:
+        if self.beta != 0.0 and self.lora is None:  # LoRA: the reference is the model with its adapter off (:853-856)
             self.ref_model = build_model(self.model.cfg, self.device, seed=None, trainable=False,
                                          dtype=self.model.dtype)
             self.ref_model.copy_from(self.model)
-        self.optimizer = FlatAdamW(self.model.numel, self.device, lr=a.learning_rate,
+        flat, _ = self._trainable()
+        self.optimizer = FlatAdamW(flat.numel(), self.device, lr=a.learning_rate,
                                    betas=(a.adam_beta1, a.adam_beta2), eps=a.adam_epsilon,
                                    weight_decay=a.weight_decay, max_grad_norm=a.max_grad_norm,
                                    no_decay_ranges=self.model.no_decay_ranges())
-        self.optimizer.master.copy_(self.model.flat.float())
+        self.optimizer.master.copy_(flat.float())
         self.state = new_state(self.rank, self.local_rank)
         self._step = 0
         self._buffered_inputs = None
@@ -369,6 +386,20 @@ class GRPOTrainer:
         self._ref_version = 0    # TR-DPO syncs of the reference so far
         self.callback_handler = CallbackHandler(callbacks, self)
         self.control = self.callback_handler.call("on_init_end")
+
+    def _trainable(self) -> tuple:
+        """(parameter buffer, gradient buffer) the optimizer updates: the model's flat
+        buffers, or with peft_config the adapter's (fp32 gradients)."""
+        m = self.model
+        return (m.adapter, m.adapter_grad) if self.lora is not None else (m.flat, m.grad)
+
+    def _ref_logps(self, batch: dict) -> torch.Tensor:
+        """Reference log-probs (:1871-1899): the frozen copy, or with peft_config the
+        policy under its disabled adapter (:1886)."""
+        if self.lora is not None:
+            with self.model.adapters_disabled():
+                return self._score_logps(self.model, batch)
+        return self._score_logps(self.ref_model, batch)
 
     # ------------------------------------------------------------------ callbacks (transformers Trainer API)
     def add_callback(self, callback):
@@ -474,7 +505,9 @@ class GRPOTrainer:
         # the policy itself: bf16 on the DecodeEngine, an fp32 policy on the fp32
         # RefDecodeEngine (the reference generates in the model dtype, :1793-1810)
         # one engine per batch size (training and evaluation batches differ), built once
-        gm = self.model
+        # LoRA: the engine reads the merged weights W + s B A, re-merged here once per generation
+        # (the generator sync of :1335-1378), before generate() folds / packs them
+        gm = self.model.decode_view() if self.lora is not None else self.model
         e = self._engines.get(B)
         if e is None or e.Pmax < P or e.model is not gm:
             Pmax = max(P, self.max_prompt_length or P) if (self.max_prompt_length or 0) <= 4096 else P
@@ -556,7 +589,7 @@ class GRPOTrainer:
         if eager_old:
             out["old_per_token_logps"] = self._score_logps(self.model, out)
         if eager_ref:
-            out["ref_per_token_logps"] = self._score_logps(self.ref_model, out)
+            out["ref_per_token_logps"] = self._ref_logps(out)
         m = self._metrics[mode]
         # per generation, resolved at the next log (no host sync here): this rank's
         # lengths / EOS flags (gathered across ranks at the log, :1945-1960), its
@@ -771,7 +804,7 @@ class GRPOTrainer:
         R = seg.numel()
         row_scale = torch.full((R,), 1.0 / GA, device=self.device)
         if any(take_ref):
-            ref_lp = self._score_logps(self.ref_model, batch)
+            ref_lp = self._ref_logps(batch)
             batch["ref_per_token_logps"] = self._merge_rows(batch.get("ref_per_token_logps"), ref_lp, take_ref, rows)
         _trace("loss inputs ready")
         with torch.set_grad_enabled(train):
@@ -886,7 +919,8 @@ class GRPOTrainer:
                      for m in micro)
         # DP: each layer's gradient all-reduce starts as soon as the (last) backward
         # pass has finished that layer, overlapped with the rest of the backward
-        ar = swh_dist.OverlappedAllReduce(self.model.grad, dw_streams(self.device)) if self.world > 1 else None
+        ar = (swh_dist.OverlappedAllReduce(self.model.grad, dw_streams(self.device))
+              if self.world > 1 and self.lora is None else None)
         groups = [micro] if (a.fuse_micro_batches and tokens <= a.fuse_token_budget) else [[m] for m in micro]
         for gi, grp in enumerate(groups):
             if ar is not None and gi == len(groups) - 1:
@@ -897,9 +931,12 @@ class GRPOTrainer:
                 self.model.on_layer_grads = None
         if ar is not None:
             ar.finish()
+        flat, grad = self._trainable()
+        if self.lora is not None and self.world > 1:  # the adapter gradients are small: one all-reduce, no overlap
+            swh_dist.allreduce_mean_(grad)
         lr = self._current_lr()
         self.control = self.callback_handler.call("on_pre_optimizer_step")
-        norm = self.optimizer.step(self.model.grad, model_out=self.model.flat, lr=lr)
+        norm = self.optimizer.step(grad, model_out=flat, lr=lr)
         self.control = self.callback_handler.call("on_optimizer_step")
         self.state.global_step += 1
         _trace(f"optimizer step {self.state.global_step}")
@@ -1035,9 +1072,23 @@ class GRPOTrainer:
         if out is None:
             raise ValueError("save_model needs an output_dir")
         if self.rank == 0:
-            ck.save_pretrained(self.model, out, eos_token_id=self.eos_token_id, pad_token_id=self.pad_token_id)
+            if self.lora is not None:  # peft's save_pretrained: the adapter only
+                ck.save_adapter(self.model, out, self._base_name)
+            else:
+                ck.save_pretrained(self.model, out, eos_token_id=self.eos_token_id, pad_token_id=self.pad_token_id)
             if self.processing_class is not None and hasattr(self.processing_class, "save_pretrained"):
                 self.processing_class.save_pretrained(out)
+        swh_dist.barrier()
+
+    def save_merged(self, output_dir: str):
+        """With peft_config: the full model W + s B A in transformers layout (the merge
+        in fp32, rounded once to the model dtype) — peft's merge_and_unload + save."""
+        from . import checkpoint as ck
+        if self.lora is None:
+            raise ValueError("save_merged needs a trainer built with peft_config (save_model writes the full model)")
+        if self.rank == 0:
+            ck.save_pretrained(self.model, output_dir, eos_token_id=self.eos_token_id, pad_token_id=self.pad_token_id,
+                               state_dict=self.model.merged_hf_state_dict())
         swh_dist.barrier()
 
     def create_model_card(self, model_name: Optional[str] = None, dataset_name: Optional[str] = None, tags=None):
@@ -1071,11 +1122,14 @@ class GRPOTrainer:
             torch.save(self._resume_state(), os.path.join(d, ck.trainer_state_file(self.rank)))
         if self.rank == 0:
             if not a.save_only_model:
-                torch.save(ck.optimizer_state_dict(self.model, self.optimizer, a.weight_decay),
-                           os.path.join(d, "optimizer.pt"))
+                if self.lora is None:
+                    torch.save(ck.optimizer_state_dict(self.model, self.optimizer, a.weight_decay),
+                               os.path.join(d, "optimizer.pt"))
+                else:  # the fp32 adapter master and moments ride in swh_master.safetensors (save_master)
+                    torch.save({"step": torch.tensor(self.optimizer.step_count)}, os.path.join(d, "optimizer.pt"))
                 torch.save(ck.scheduler_state_dict(self.state.global_step, a.learning_rate, self._schedule()),
                            os.path.join(d, "scheduler.pt"))
-                ck.save_master(self.optimizer, d)
+                ck.save_master(self.optimizer, d, moments=self.lora is not None)
                 if self.ref_model is not None and a.sync_ref_model:  # the mixed reference is trainer state
                     from safetensors.torch import save_file
                     save_file({"ref": self.ref_model.flat.detach().cpu()}, os.path.join(d, "swh_ref.safetensors"))
@@ -1120,7 +1174,9 @@ class GRPOTrainer:
         import json
 
         from . import checkpoint as ck
-        if os.path.exists(os.path.join(d, "swh_master.safetensors")):
+        if self.lora is not None:
+            ck.load_adapter_checkpoint(self.model, self.optimizer, d)
+        elif os.path.exists(os.path.join(d, "swh_master.safetensors")):
             from safetensors.torch import load_file
             self.optimizer.master.copy_(load_file(os.path.join(d, "swh_master.safetensors"))["master"])
             self.model.flat.copy_(self.optimizer.master)
@@ -1132,7 +1188,7 @@ class GRPOTrainer:
             from safetensors.torch import load_file
             self.ref_model.flat.copy_(load_file(ref_path)["ref"])
         opt_path = os.path.join(d, "optimizer.pt")
-        if os.path.exists(opt_path):
+        if os.path.exists(opt_path) and self.lora is None:
             ck.load_optimizer_state_dict(self.model, self.optimizer, torch.load(opt_path, weights_only=True))
         with open(os.path.join(d, "trainer_state.json")) as f:
             js = json.load(f)
